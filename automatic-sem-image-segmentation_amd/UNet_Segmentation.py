@@ -190,8 +190,8 @@ class UNetModel:
         # hardware queues round-robin, so the indices decide which chains share a queue); SS_UNET_STREAMS="w,b1,b2,b3,b4" overrides
         env = os.environ.get("SS_UNET_STREAMS")
         self.stream_indices = [int(v) for v in env.split(",")] if env else None
-        # OPT-IN (graph = True / SS_UNET_GRAPH=1): the step -- forward, loss, backward on its side streams, Adam -- captured ONCE per input
-        # shape into a hipGraph (torch.cuda.graph) and replayed: same kernels, same order per stream, same bits
+        # OPT-IN (graph = True / SS_UNET_GRAPH=1): the step -- forward, loss, backward, Adam -- captured ONCE per input shape on ONE
+        # stream into a hipGraph (torch.cuda.graph) and replayed: same kernels, same accumulation order, same bits
         # (tests/test_nets_gpu.py); what changes per step enters through device memory (the input tiles, Adam's alpha).  Not the
         # default: at per-GPU batch 1 (the 8-GPU share of BASELINE config 4: one 512 x 512 tile, ~1100 launches) the step is paced by
         # the per-dispatch cost on BOTH sides -- eager: 12.8 ms of host issue, 11.1 ms wall; replayed: hipGraphLaunch of the
@@ -311,12 +311,21 @@ class UNetModel:
             st["x"].copy_(self._as_f32(batch[0], st["x"]))
             st["y"].copy_(self._as_f32(batch[1], st["y"]))
             iters = self.optimizer.iterations
+            # captured on ONE stream: the weight gradients and the ResPath branches stay on the capturing stream instead of the eager
+            # step's side streams (same kernels, same accumulation order, same bits: test_unet_respath_branches_equal_the_inline_step).
+            # A capture that forks onto side streams -- their waits, events and record_stream uses -- becomes a multi-branch graph the
+            # runtime replays on parallel streams of its own; replaying that graph crashed the process inside hipGraphLaunch.
+            sides = (self.wgrad_side_stream, self.branch_streams, self.refresh_side_stream)
+            self.wgrad_side_stream = self.branch_streams = self.refresh_side_stream = False
             try:
-                with capture_scope() as scope, torch.cuda.graph(st["graph"]):
-                    from .engine import convert
-                    xa = convert(Act(st["x"], requires_grad=False), self.act_dtype)
-                    ya = convert(Act(st["y"], requires_grad=False), self.act_dtype)
-                    self._issue_step(xa, ya, alpha_dev=st["alpha"])
+                try:
+                    with capture_scope() as scope, torch.cuda.graph(st["graph"]):
+                        from .engine import convert
+                        xa = convert(Act(st["x"], requires_grad=False), self.act_dtype)
+                        ya = convert(Act(st["y"], requires_grad=False), self.act_dtype)
+                        self._issue_step(xa, ya, alpha_dev=st["alpha"])
+                finally:
+                    self.wgrad_side_stream, self.branch_streams, self.refresh_side_stream = sides
             except Exception as e:          # noqa: BLE001  -- a capture this runtime refuses: say so once, stay eager (same results)
                 self.optimizer.iterations = iters
                 self.graph = False

@@ -29,6 +29,7 @@ import importlib
 import json
 import os
 os.environ.setdefault("HIP_FORCE_DEV_KERNARG", "1")          # before the HIP runtime initialises (see _lib.py)
+import random
 import statistics
 import sys
 import time
@@ -46,6 +47,29 @@ G_FWD_GF = {256: 102.29, 384: 230.15, 512: 409.16, 1024: 1636.65}   # SURVEY.md 
 D_FWD_GF = {256: 7.88, 384: 18.32, 512: 33.09, 1024: 135.56}
 U_FWD_GF = {256: 10.56, 384: 23.76, 512: 42.24, 1024: 168.94}
 UNET_BYTES_PER_TILE_512 = 6.5e9                                      # fp32 activations, 512x512
+DUMP_MAX_PER_NET = 2 * 1024 * 1024          # --dump-outputs: float32 weight values kept per network (5 networks: <= 40 MB in all)
+DUMP_SAMPLE_SEED = 20240
+
+
+def dump_outputs(out_dir, metrics, nets):
+    """--dump-outputs: metrics = {trainer: the dict its last timed train_step returned}, nets = {name: network}.  Each metric goes to
+    <trainer>_<metric>.npy (float64 scalar); each network's weights after the step (get_weights order, concatenated) to
+    weights_<name>.npy (float32), all of them if there are at most DUMP_MAX_PER_NET, else the values at DUMP_MAX_PER_NET positions drawn
+    without replacement by np.random.default_rng(DUMP_SAMPLE_SEED) (sorted) -- the same positions for the same network shape."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    written = []
+    for trainer, m in metrics.items():
+        for k, v in sorted(m.items()):
+            np.save(os.path.join(out_dir, f"{trainer}_{k}.npy"), np.asarray(v, dtype=np.float64))
+            written.append(f"{trainer}_{k}")
+    for name, net in nets.items():
+        w = np.concatenate([np.asarray(a, dtype=np.float32).ravel() for a in net.get_weights()])
+        if w.size > DUMP_MAX_PER_NET:
+            w = w[np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(w.size, DUMP_MAX_PER_NET, replace=False))]
+        np.save(os.path.join(out_dir, f"weights_{name}.npy"), w)
+        written.append(f"weights_{name}")
+    return written
 
 
 def synthetic_tiles(n, size, seed):
@@ -138,7 +162,13 @@ def main():
     ap.add_argument("--tables", default=None, help="where the per-kernel tables go (default: profiles/bench_tables_last.json)")
     ap.add_argument("--skip-unet", action="store_true", help="diagnostics only: time the CycleGAN step alone")
     ap.add_argument("--only-unet", action="store_true", help="diagnostics only: time the UNet step alone")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the LAST timed step computed as DIR/<name>.npy: the metrics each train_step "
+                         "returned (float64) and every network's weights after that step (float32; a fixed, seeded sample of at most "
+                         f"{DUMP_MAX_PER_NET} values per network), so that two builds can be compared output for output")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     preset = {4: dict(size=512, gb=8, dtype="f32", ck=False, cg=True, un=True), 2: dict(size=256, gb=16, dtype="bf16", ck=False, cg=False, un=True),
               3: dict(size=256, gb=4, dtype="f32", ck=False, cg=True, un=False), 5: dict(size=1024, gb=8, dtype="f16", ck=True, cg=True, un=True)}[args.config]
     args.size = args.size or preset["size"]
@@ -183,7 +213,9 @@ def main():
     D.enable_overlap([ga, gb, da, db, unet])     # bucketed gradient all-reduce launched during backward
     if world > 1:
         D.enable_sync_bn(True)      # whole-(global)-batch BatchNorm statistics = the single-device semantics of the reference
-    model = CG.CycleGanModel(ga, gb, da, db, image_pool_a=CG.ImagePool(2, 50), image_pool_b=CG.ImagePool(2, 50))
+    # the pools' draws from seeded generators of their own: the same arguments give the same inputs and decisions in every run
+    model = CG.CycleGanModel(ga, gb, da, db, image_pool_a=CG.ImagePool(2, 50, rng=random.Random(101)),
+                             image_pool_b=CG.ImagePool(2, 50, rng=random.Random(102)))
     model.compile(OPT.Adam(2e-4, beta_1=0.5), OPT.Adam(2e-4, beta_1=0.5), OPT.Adam(2e-4, beta_1=0.5), OPT.Adam(2e-4, beta_1=0.5))
     umodel = UN.UNetModel(unet, 9.0, OPT.Adam(1e-3))
 
@@ -204,6 +236,7 @@ def main():
     # step it takes streams apart from the chains')
 
     full_inputs = (a, b, ux, uy)
+    last_metrics = {}          # trainer -> what its latest train_step returned (--dump-outputs)
 
     def step(cyclegan=not args.only_unet, unet_=not args.skip_unet, overlap=overlap_unet, inputs=None):
         a, b, ux, uy = inputs if inputs is not None else full_inputs
@@ -225,9 +258,9 @@ def main():
             model._scalars.cpu()          # the step's one device->host read (both steps' scalars are final behind the join)
             return
         if cyclegan:
-            model.train_step((a, b))
+            last_metrics["cyclegan"] = model.train_step((a, b))
         if unet_:
-            umodel.train_step((ux.t, uy.t))
+            last_metrics["unet"] = umodel.train_step((ux.t, uy.t))
 
     def barrier():
         if world > 1:
@@ -256,8 +289,15 @@ def main():
 
     for _ in range(args.warmup):
         step()
+    last_metrics.clear()
     elapsed, per_step = timed(args.steps)
     elapsed = max_over_ranks(elapsed)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # before any further leg moves the weights on (outside the timed region)
+        ran = ([("gen_a", ga), ("gen_b", gb), ("disc_a", da), ("disc_b", db)] if not args.only_unet else []) + \
+              ([("unet", unet)] if not args.skip_unet else [])
+        dumped = dump_outputs(args.dump_outputs, {k: v for k, v in last_metrics.items() if v}, dict(ran))
     median_ms = max_over_ranks(statistics.median(per_step)) * 1e3
 
     extras = {}
@@ -516,6 +556,8 @@ def main():
             out["tables_path"] = os.path.relpath(tpath, REPO)
         except OSError:
             out["tables_path"] = None
+        if dumped is not None:
+            out.update(dump_outputs_dir=args.dump_outputs, dump_outputs_arrays=len(dumped))
         print(json.dumps(out), flush=True)
     if world > 1:
         torch.distributed.destroy_process_group()
